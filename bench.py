@@ -456,7 +456,18 @@ def cpu_baseline_regional(preset, H, W, budget_s=28.0):
 
 
 # ---- part 1: training ----------------------------------------------------------------------------------------------
-def run_train(args, rank, world, device):
+def train_outputs(engine, trainer, out):
+    """What the last timed optimisation step handed back: its loss and concept-row norm, the trained tensors after its update
+    (concept rows; every LoRA factor, text encoder then UNet, flattened in module order) and the gradient bucket it applied."""
+    def flat(ps):
+        return torch.cat([p.detach().float().reshape(-1) for p in ps])
+    return dict(train_loss=out['loss'], train_norm_mean=out['Norm_mean'], train_concept_embedding=trainer.concept_embedding,
+                train_text_encoder_lora=flat(p for l in trainer.text_encoder_lora for p in l.parameters()),
+                train_unet_lora=flat(p for l in trainer.unet_lora for p in l.parameters()),
+                train_grad_bucket=engine.bucket.flat)
+
+
+def run_train(args, rank, world, device, outputs=None):
     from mixofshow.hip import profiler
     from mixofshow.pipelines.train_loop import TrainEngine
     B, size = args.batch, args.size
@@ -517,10 +528,12 @@ def run_train(args, rank, world, device):
         t0 = time.perf_counter()
         marks[0].record()
         for i in range(args.steps):
-            engine.step(next_batch(i))
+            last = engine.step(next_batch(i))
             marks[i + 1].record()                   # device-side step boundaries: no host sync inside the region
         _sync_barrier(world)
         dt = _max_over_ranks(time.perf_counter() - t0, world, device)
+    if outputs is not None:                         # copied before any later step overwrites them (the replayed loss is static)
+        outputs.update({k: v.detach().float().cpu() for k, v in train_outputs(engine, trainer, last).items()})
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     spread = [round(per_step[0], 2), round(statistics.median(per_step), 2), round(per_step[-1], 2)] if per_step else None
     # what the HOST needs per step, outside the timed region: with the device idle at the start of a step nothing the host does
@@ -696,11 +709,12 @@ def synthetic_keypose_adapter(pipe, height, width, device, dtype, seed=16):
     return ad, image, stds
 
 
-def run_regional(args, rank, world, device, steps=None, warmup=None):
+def run_regional(args, rank, world, device, steps=None, warmup=None, outputs=None):
     """`value` = latency of the call AS THE REFERENCE'S CALL RETURNS IT (regionally_controlable_sampling.py:40-52,
     pipeline_regionally_t2iadapter.py:474-546, 582-595): T2I-Adapter forward on a pose image + region-weight rule, 50
     regional UNet steps, VAE decode at 512x768, PIL conversion on the host. `value_ms_latent` = the same 50 steps with
-    precomputed adapter states and `output_type='latent'` (the round-1..3 line) for continuity."""
+    precomputed adapter states and `output_type='latent'` (the round-1..3 line) for continuity. `outputs` (a dict) receives the
+    image of the last timed call (H, W, 3; 0..255) and the latents of the last timed latent call."""
     from mixofshow.hip import profiler
     H, W = int(getattr(args, 'height', 512)), int(getattr(args, 'width', 768))
     steps = steps or args.steps
@@ -740,9 +754,11 @@ def run_regional(args, rank, world, device, steps=None, warmup=None):
     dt, images = timed(steps)
     sample(graph, image_out=False)
     dt_lat, out = timed(steps, image_out=False)
+    import numpy as np
+    if outputs is not None:
+        outputs.update(regional_image=np.asarray(images[0], dtype=np.float32), regional_latents=out.float().cpu())
     graphed = bool(getattr(pipe, 'last_call_graphed', False))
     eager_steps = int(getattr(pipe, 'last_call_replay_from', 1)) if graphed else 50     # (read before the profiled eager pass)
-    import numpy as np
     img_ok = (len(images) == 1 and images[0].size == (W, H) and bool(np.isfinite(np.asarray(images[0], dtype=np.float32)).all()))
     recs = []
     with profiler.profile(recs):                     # HIP events are recorded at launch: profiled pass runs eagerly
@@ -838,7 +854,29 @@ def fusion_roofline(lsq, gram):
     return out
 
 
-def run_fusion(args, rank, world, device):
+def seeded_sample(named, per_tensor, seed=0):
+    """A fixed sample of a large output: `per_tensor` elements drawn (seeded, with replacement) from each named tensor in
+    name order, concatenated."""
+    g = torch.Generator().manual_seed(seed)
+    parts = []
+    for _, t in sorted(named, key=lambda kv: kv[0]):
+        idx = torch.randint(t.numel(), (per_tensor, ), generator=g)
+        parts.append(t.detach().reshape(-1)[idx.to(t.device)].float().cpu())
+    return torch.cat(parts)
+
+
+def fusion_outputs(pipe, new_concept_cfg):
+    """What the last fusion handed back: the fused concept rows of the token table, and a seeded sample of the fused attention
+    weights of the text encoder and the UNet (the layers the fusion rewrites; the full model is ~1 G parameters)."""
+    ids = [i for c in new_concept_cfg.values() for i in c['concept_token_ids']]
+    table = pipe.text_encoder.get_input_embeddings().weight
+    return dict(fusion_concept_embedding=table[ids].detach().float().cpu(),
+                fusion_text_encoder_attn_sample=seeded_sample(
+                    [kv for kv in pipe.text_encoder.named_parameters() if 'attn' in kv[0]], 4096, seed=1),
+                fusion_unet_attn_sample=seeded_sample([kv for kv in pipe.unet.named_parameters() if 'attn' in kv[0]], 4096, seed=2))
+
+
+def run_fusion(args, rank, world, device, outputs=None):
     """configs[3]: gradient_fusion.compose_concepts on 14 synthetic ED-LoRAs, iters 500 (CLIP, cross-K/V) / 50 (spatial)
     as fuse.sh:8-9; a "step" is one complete fusion. Roofline: the Gram kernel. cpu_baseline: ONE level-0 spatial layer
     (n = 81,920 rows = one concept, 320 -> 320) through the reference-semantics L-BFGS on stored features."""
@@ -857,12 +895,15 @@ def run_fusion(args, rank, world, device):
         t0 = time.perf_counter()
         if profiling:
             profiler.begin()
-        gf.compose_concepts(cfg, args.textenc_iters, args.unet_iters, f'synthetic://{args.preset}?seed=0', tmp, 'bench',
-                            device, save=False)
+        fused = gf.compose_concepts(cfg, args.textenc_iters, args.unet_iters, f'synthetic://{args.preset}?seed=0', tmp, 'bench',
+                                    device, save=False)
         torch.cuda.synchronize()
         if profiling:
             recs.extend(profiler.end())
         dt = time.perf_counter() - t0
+        if outputs is not None and i == args.warmup + args.steps - 1:
+            outputs.update(fusion_outputs(*fused))
+        del fused
         _log(f'fusion pass {i}: {dt:.1f}s')
         if i >= args.warmup:
             times.append(dt)
@@ -1011,6 +1052,49 @@ def write_full_record(res):
     return path
 
 
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs DIR: every array in `outputs` -> DIR/<name>.npy, float64 kept, anything else as float32; at most
+    DUMP_LIMIT_BYTES in all. The inputs of a run are seeded, so two builds run with the same arguments compare file by file."""
+    import numpy as np
+    arrays = {}
+    for name, v in outputs.items():
+        a = v.detach().cpu().numpy() if torch.is_tensor(v) and v.dtype == torch.float64 else \
+            v.detach().float().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        arrays[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f'--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte bound')
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f'{name}.npy'), a)
+    _log(f'outputs of the last timed step ({len(arrays)} arrays, {total} bytes) -> {path}')
+
+
+def deterministic_kernels():
+    """The convolutions the library does not run (VAE encoder / decoder levels, the T2I-Adapter) go to MIOpen, whose solver
+    choice for a shape differs between its first call and later ones and between processes: two runs with the same inputs
+    then differ in the last bits, and the difference grows over a training run or 50 sampling steps. Deterministic solvers
+    (and torch's deterministic implementations) make the train outputs and the regional latents repeat exactly from run to
+    run; the T2I-Adapter's features still differ between processes, so the regional image does not yet. They cost time:
+    MIOpen's immediate-mode solvers for these shapes are slow (train step 32 -> 168 ms on MI355X), so only --dump-outputs
+    runs use them.
+    Immediate mode takes a shape's solver from the user find-db when it holds one, and that database is filled by earlier
+    searching runs on the same machine (any plain bench, test or training run): the run gets an empty one of its own, so
+    that the choice depends on the installed MIOpen alone and not on what ran before. Call before MIOpen is first used."""
+    import atexit
+    import shutil
+    import tempfile
+    db = tempfile.mkdtemp(prefix='mos_miopen_db_')
+    atexit.register(shutil.rmtree, db, ignore_errors=True)
+    os.environ['MIOPEN_USER_DB_PATH'] = db
+    torch.backends.cudnn.deterministic = True
+    torch.backends.cudnn.benchmark = False
+    torch.use_deterministic_algorithms(True, warn_only=True)     # (also fills fresh allocations: nothing reads stale memory)
+
+
 def _self_launch(args):
     """`python bench.py --gpus N` without a launcher: start the N ranks ourselves (one per GPU over RCCL), fail loudly
     if the node cannot run them."""
@@ -1056,11 +1140,16 @@ def main():
     ap.add_argument('--concepts', type=int, default=14)
     ap.add_argument('--textenc-iters', type=int, default=500)
     ap.add_argument('--unet-iters', type=int, default=50)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32/64); '
+                    'the run uses deterministic convolution solvers (slower) so that its outputs repeat exactly')
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 2 if args.mode == 'fusion' else 8
     if args.warmup is None:
         args.warmup = 1 if args.mode == 'fusion' else 3
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         _self_launch(args)
     from mixofshow.parallel import dp
@@ -1073,10 +1162,13 @@ def main():
         sys.exit(2)
     device = torch.device('cuda', local)
     torch.cuda.set_device(device)
+    if args.dump_outputs:
+        deterministic_kernels()
+    outputs = {} if args.dump_outputs else None
     if args.mode == 'train':
-        res = run_train(args, rank, world, device)
+        res = run_train(args, rank, world, device, outputs)
         if world == 1 and not args.no_regional:
-            reg = run_regional(args, rank, world, device, steps=min(args.steps, 3), warmup=min(args.warmup, 1))
+            reg = run_regional(args, rank, world, device, steps=min(args.steps, 3), warmup=min(args.warmup, 1), outputs=outputs)
             res['regional'] = dict(value_ms=reg['value'], value_ms_image=reg['value_ms_image'],
                                    value_ms_latent=reg['value_ms_latent'], cold_call_ms=reg['cold_call_ms'],
                                    metric=reg['metric'], steps=reg['steps'], warmup=reg['warmup'],
@@ -1088,11 +1180,13 @@ def main():
         else:
             res['regional'] = None
     elif args.mode == 'regional':
-        res = run_regional(args, rank, world, device)
+        res = run_regional(args, rank, world, device, outputs=outputs)
     else:
-        res = run_fusion(args, rank, world, device)
+        res = run_fusion(args, rank, world, device, outputs)
     res['parity'] = parity_figures()
     if rank == 0:
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         full = write_full_record(res)
         sys.stderr.flush()
         print(compact_line(res, full), flush=True)      # the LAST stdout line, <= COMPACT_LIMIT bytes

@@ -4,7 +4,7 @@ CPU restatement (plain torch, any float dtype; run it in fp32/fp64 for ground tr
 ED-LoRA hot path. Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this.
 The product package (mix-of-show_amd/mixofshow) never does.
 
-Pinned against the REAL reference code: tests/golden/make_golden.py imports /root/reference with stubbed
+Pinned against the REAL reference code: tests/golden/make_golden.py imports the reference checkout with stubbed
 third-party modules and records its outputs; tests/test_oracle_golden.py checks this file against them.
 What stays "from memory" is the diffusers `Attention` helper semantics (oracle/attention_shim.py).
 

@@ -1,4 +1,4 @@
-"""Generate golden vectors by executing the REAL reference code (read-only at /root/reference).
+"""Generate golden vectors by executing the REAL reference code (a read-only checkout named by MOS_REFERENCE_DIR).
 
 Runs only in the authoring container (the reference does not exist on the GPU box); the outputs are
 committed as small fixtures next to this script and pin oracle/*.py (tests/test_oracle_golden.py).
@@ -31,7 +31,8 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.normpath(os.path.join(HERE, '..', '..'))
-REF = '/root/reference'
+# a checkout of the reference project (read-only), named by MOS_REFERENCE_DIR
+REF = os.path.abspath(os.environ.get('MOS_REFERENCE_DIR', 'Mix-of-Show'))
 STUB_ROOTS = ('diffusers', 'omegaconf', 'torchvision', 'cv2', 'IPython', 'xformers')
 
 

@@ -1,5 +1,5 @@
 """Golden vectors of the DATA transforms, produced by EXECUTING the reference's own classes
-(/root/reference/mixofshow/data/pil_transform.py and lora_dataset.py, read-only, unmodified):
+(<reference>/mixofshow/data/pil_transform.py and lora_dataset.py, read-only, unmodified):
 
   G9  ShuffleCaption / EnhanceText (:257-364)     pure Python -- nothing but the reference runs
   G10 HumanResizeCropFinalV3 (:125-195), ResizeFillMaskNew (:198-254), PairRandomCrop, PairCompose
@@ -11,7 +11,7 @@ same arrangement as oracle/attention_shim.py for diffusers. What the goldens the
 the order in which Python's `random` and torch's generator are consumed, the crop-branch logic, canvas placement, the
 `/255` and 1/8-mask steps, caption handling, dataset item layout.
 
-Runs only where /root/reference exists.  Usage:  python tests/golden/make_golden_data.py [output.pt]
+Runs only where a reference checkout exists.  Usage:  MOS_REFERENCE_DIR=<checkout> python tests/golden/make_golden_data.py [output.pt]
 """
 import hashlib
 import json
@@ -26,7 +26,8 @@ from PIL import Image
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.normpath(os.path.join(HERE, '..', '..'))
-REF = '/root/reference'
+# a checkout of the reference project (read-only), named by MOS_REFERENCE_DIR
+REF = os.path.abspath(os.environ.get('MOS_REFERENCE_DIR', 'Mix-of-Show'))
 
 
 def _install_vision_modules():

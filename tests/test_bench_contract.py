@@ -179,3 +179,88 @@ def test_jpeg_data_pipeline_feeds_the_training_step(emulated_hip, tmp_path):
     engine = TrainEngine(tr, opt, total_iter=10, mixed_precision='no')
     out = engine.step(b)
     assert torch.isfinite(out['loss']) and engine.global_step == 1
+
+
+def test_dump_outputs_writes_float_arrays_within_the_bound(tmp_path):
+    """`bench.py --dump-outputs DIR`: one DIR/<name>.npy per output, float32 (float64 kept), the total bounded."""
+    import numpy as np
+    import torch
+    import bench
+    outs = dict(loss=torch.tensor(0.25), rows=torch.arange(6, dtype=torch.float16).reshape(2, 3),
+                image=np.full((4, 5, 3), 7, dtype=np.uint8), solve=torch.ones(3, dtype=torch.float64))
+    bench.dump_outputs(str(tmp_path / 'd'), outs)
+    got = {f[:-4]: np.load(tmp_path / 'd' / f) for f in sorted(os.listdir(tmp_path / 'd'))}
+    assert set(got) == set(outs)
+    assert got['loss'].dtype == np.float32 and got['loss'].shape == () and got['loss'] == 0.25
+    assert got['rows'].dtype == np.float32 and np.array_equal(got['rows'], np.arange(6).reshape(2, 3))
+    assert got['image'].dtype == np.float32 and got['image'].shape == (4, 5, 3) and (got['image'] == 7).all()
+    assert got['solve'].dtype == np.float64
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / 'big'), dict(x=torch.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1)))
+    assert not os.path.exists(tmp_path / 'big')
+
+
+def test_seeded_sample_is_fixed():
+    import torch
+    import bench
+    named = [('b', torch.arange(1000.)), ('a', torch.arange(50.) * -1)]
+    s1, s2 = bench.seeded_sample(named, 16, seed=3), bench.seeded_sample(named[::-1], 16, seed=3)
+    assert s1.shape == (32, ) and s1.dtype == torch.float32 and torch.equal(s1, s2)
+    assert (s1[:16] <= 0).all() and (s1[16:] >= 0).all()           # name order: 'a' first
+
+
+def test_steps_must_be_positive():
+    """`--steps` is the number of timed steps and `ms_per_step` divides by it: zero steps is refused before any work."""
+    import subprocess
+    import sys
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0'], capture_output=True, text=True,
+                       timeout=300)
+    assert p.returncode == 2 and '--steps' in p.stderr and p.stdout.strip() == ''
+
+
+def test_train_outputs_are_what_the_step_left(emulated_hip):
+    """`--dump-outputs` in train mode: the loss of the step, the trained tensors after its update and the gradient it applied."""
+    import torch
+    import bench
+    from mixofshow.pipelines.train_loop import TrainEngine
+    from tests.test_host_cpu import _batch, _trainer
+    tr = _trainer()
+    opt = dict(optim_g=dict(type='AdamW', lr=0.0, weight_decay=0.01, betas=[0.9, 0.999]), emb_norm_threshold=0.55)
+    engine = TrainEngine(tr, opt, total_iter=10, mixed_precision='no')
+    out = engine.step(_batch())
+    o = bench.train_outputs(engine, tr, out)
+    assert torch.equal(o['train_loss'], out['loss']) and torch.equal(o['train_concept_embedding'], tr.concept_embedding)
+    n_te = sum(p.numel() for l in tr.text_encoder_lora for p in l.parameters())
+    n_un = sum(p.numel() for l in tr.unet_lora for p in l.parameters())
+    assert o['train_text_encoder_lora'].numel() == n_te and o['train_unet_lora'].numel() == n_un
+    assert o['train_grad_bucket'].numel() == tr.concept_embedding.numel() + n_te + n_un
+    assert float(o['train_grad_bucket'].abs().sum()) > 0
+
+
+def test_bench_selects_deterministic_kernels():
+    """Two `--dump-outputs` runs with the same arguments must compute the same outputs: main() asks for deterministic MIOpen
+    solvers and torch implementations before any work on the device."""
+    import torch
+    import torch.utils.deterministic
+    import bench
+    src = open(os.path.join(ROOT, 'bench.py')).read()
+    main = src[src.index('def main():'):]
+    assert main.index('if args.dump_outputs:\n        deterministic_kernels()') < main.index('run_train(')
+    saved = (torch.backends.cudnn.deterministic, torch.backends.cudnn.benchmark, torch.are_deterministic_algorithms_enabled(),
+             torch.is_deterministic_algorithms_warn_only_enabled(), torch.utils.deterministic.fill_uninitialized_memory)
+    saved_db = os.environ.get('MIOPEN_USER_DB_PATH')
+    try:
+        bench.deterministic_kernels()
+        db = os.environ['MIOPEN_USER_DB_PATH']          # an empty solver database of the run's own
+        assert db != saved_db and os.path.isdir(db) and os.listdir(db) == []
+        assert torch.backends.cudnn.deterministic and not torch.backends.cudnn.benchmark
+        assert torch.are_deterministic_algorithms_enabled() and torch.utils.deterministic.fill_uninitialized_memory
+    finally:
+        torch.backends.cudnn.deterministic, torch.backends.cudnn.benchmark = saved[:2]
+        torch.use_deterministic_algorithms(saved[2], warn_only=saved[3])
+        torch.utils.deterministic.fill_uninitialized_memory = saved[4]
+        if saved_db is None:
+            os.environ.pop('MIOPEN_USER_DB_PATH', None)
+        else:
+            os.environ['MIOPEN_USER_DB_PATH'] = saved_db
+

@@ -5,7 +5,6 @@ random generators afterwards -- i.e. the same number of draws in the same order)
 import importlib.util
 import os
 import random
-import subprocess
 import sys
 
 import numpy as np
@@ -92,13 +91,3 @@ def test_lora_dataset_items_vs_reference_golden(gold, tmp_path):
                     else:
                         assert abs(float(v.double().mean()) - w['mean']) < 1e-7, (i, k)
 
-
-@pytest.mark.skipif(not os.path.isdir('/root/reference/mixofshow'), reason='reference tree not present')
-def test_reference_data_golden_regenerates_bit_identical(tmp_path):
-    out = tmp_path / 'd.pt'
-    r = subprocess.run([sys.executable, os.path.join(GOLDEN_DIR, 'make_golden_data.py'), str(out)], cwd='/tmp',
-                       env=dict(os.environ, PYTHONHASHSEED='0'), capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    from tests.test_reference_golden_recipe import _diff
-    new, old = torch.load(out, weights_only=False), torch.load(os.path.join(GOLDEN_DIR, 'reference_data_golden.pt'), weights_only=False)
-    assert _diff(new, old) == []

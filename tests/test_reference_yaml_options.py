@@ -1,17 +1,18 @@
 """Every YAML recipe the reference ships under options/{train,test}/** goes through the product's option loader and
 constructs the product's objects: EDLoRATrainer(**opt['models']) with a synthetic `pretrained_path` (no
 checkpoints exist offline), the three AdamW groups of TrainEngine from opt['train'], the `instance_transform` chain of the
-dataset block, the PromptDataset of the validation block. Skipped where the reference tree is absent (the GPU box)."""
+dataset block, the PromptDataset of the validation block. The recipes and the validation prompt files they name are stored
+unmodified under tests/golden/reference_recipes/, in the reference's directory layout."""
 import glob
 import os
 
 import pytest
 import torch
 
-REF = '/root/reference'
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'reference_recipes')
 TRAIN = sorted(glob.glob(os.path.join(REF, 'options', 'train', '**', '*.yml'), recursive=True))
 TEST = sorted(glob.glob(os.path.join(REF, 'options', 'test', '**', '*.yml'), recursive=True))
-pytestmark = pytest.mark.skipif(not TRAIN, reason='reference tree absent')
+assert len(TRAIN) == 6 and len(TEST) == 3, (TRAIN, TEST)     # every recipe the reference ships
 
 # the option surface the product reads (and the reference's recipes use); anything else in a shipped recipe is a gap
 TOP_KEYS = {'name', 'manual_seed', 'mixed_precision', 'gradient_accumulation_steps', 'datasets', 'models', 'path', 'train', 'val',

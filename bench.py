@@ -1,6 +1,6 @@
 """bench.py — headline benchmark of the Mix-of-Show hot path on MI355X (contract: see the task prompt / DESIGN.md).
 
-Default (`--mode train`): BOTH halves of BASELINE.json's metric in ONE JSON line.
+Default (`--mode train`): part 1 in ONE JSON line; with --full BOTH halves of BASELINE.json's metric.
   * top level = part 1, ED-LoRA train images/sec @512x512 on SD-1.5, workload = BASELINE.json configs[1] ("Single-concept
     ED-LoRA tune SD-1.5 512x512 rank=4 batch=4 on 1xMI355X"); with --gpus N>1 (one rank per GPU over RCCL, launched by
     torch.distributed.run — or by this script itself when WORLD_SIZE is unset) the same per-GPU batch => weak scaling
@@ -9,13 +9,18 @@ Default (`--mode train`): BOTH halves of BASELINE.json's metric in ONE JSON line
     embedding-norm rule. The step runs the way the product runs it by default (train_edlora.py): forward+backward
     replayed from a hipGraph.
   * `regional` = part 2, 50-step 3-region sample latency at 512x768 (configs[4]), single GPU (replicas only), with its
-    own roofline and cpu_baseline. Skipped (null) for N>1 and with --no-regional.
+    own roofline and cpu_baseline. Only with --full; skipped (null) for N>1 and with --no-regional.
 `--mode regional` prints part 2 alone; `--mode fusion` times configs[3] (gradient fusion of 14 synthetic ED-LoRAs).
+
+A plain run sets up, warms up, times the steps and prints the line. Everything else (the host-need and all-reduce timings,
+the profiled pass behind `roofline` and the kernel tables, `cpu_baseline`, the regional half of the train line, the latent-out
+regional timing, the parity figures and the verbose record) runs only with --full. --dump-outputs implies --full: it
+writes the outputs of that whole sequence (see main()).
 
 Weights: seeded random init of the exact SD-1.5 architecture, calibrated to O(1) activations (no checkpoints offline);
 data: synthetic, resident in HBM before the timed region.
 
-`roofline` describes the library kernel with the largest share of GPU time, timed with HIP events on its launch
+With --full, `roofline` describes the library kernel with the largest share of GPU time, timed with HIP events on its launch
 stream (mos_profile_*), in a short profiled pass right after the timed region so that `value` is not perturbed by
 event recording; `attention_path` is the aggregate: SURVEY 8(d)'s algorithmic attention-path FLOPs per step over the
 summed library-kernel time. `cpu_baseline` times the oracle path (oracle/*.py, plain torch fp32 = the "CPU diffusers
@@ -467,8 +472,58 @@ def train_outputs(engine, trainer, out):
                 train_grad_bucket=engine.bucket.flat)
 
 
-def run_train(args, rank, world, device, outputs=None):
+def host_need_ms(engine, next_batch, n=5):
+    """What the HOST needs per step, outside the timed region: with the device idle at the start of a step nothing the host
+    does can block on a full launch queue (inside a pipelined loop a host that runs ahead waits in hipGraphLaunch, so its loop
+    time only mirrors the device's). A replayed step needs ~5 ms of host time against ~33 ms of device time
+    (tools/host_step_breakdown.py)."""
+    host_ms = 0.0
+    for i in range(n):
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        engine.step(next_batch(i))
+        host_ms += (time.perf_counter() - t1) * 1e3 / n
+    torch.cuda.synchronize()
+    _log(f'host needs {host_ms:.2f} ms/step (device idle at step start)')
+    return host_ms
+
+
+def bucket_allreduce(engine, world, device):
+    """the one collective of the path, on its own -- the flat fp32 gradient bucket over RCCL/xGMI (latency-bound
+    at 4.5 MB). Timed on a scratch copy so the optimiser state of the run is untouched; bus bandwidth = 2(N-1)/N x bytes / time."""
+    scratch = engine.bucket.flat.clone()
+    for _ in range(5):
+        torch.distributed.all_reduce(scratch)
+    _sync_barrier(world)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    n_ar = 50
+    e0.record()
+    for _ in range(n_ar):
+        torch.distributed.all_reduce(scratch)
+    e1.record()
+    torch.cuda.synchronize()
+    us = _max_over_ranks(e0.elapsed_time(e1) * 1e3 / n_ar, world, device)
+    allreduce = dict(bytes=engine.bucket.nbytes, us=round(us, 1),
+                     busbw_gbps=round(2.0 * (world - 1) / world * engine.bucket.nbytes / (us * 1e-6) / 1e9, 2),
+                     peak_gbps_per_gpu=7 * 153.0, backend=torch.distributed.get_backend())
+    _log(f'gradient-bucket all-reduce: {allreduce}')
+    return allreduce
+
+
+def profiled_train_steps(engine, batches):
+    """Profiled pass (same workload, same process): per-kernel HIP-event timings of the library kernels over two eager steps."""
     from mixofshow.hip import profiler
+    recs = []
+    saved_graph, engine._graph = getattr(engine, '_graph', None), None   # events are recorded at launch: eager pass
+    with profiler.profile(recs):
+        for i in range(2):
+            engine.step(batches[i % 2])
+        torch.cuda.synchronize()
+    engine._graph = saved_graph
+    return recs
+
+
+def run_train(args, rank, world, device, outputs=None):
     from mixofshow.pipelines.train_loop import TrainEngine
     B, size = args.batch, args.size
     _log(f'building EDLoRATrainer (synthetic://{args.preset}) on {device}')
@@ -536,47 +591,14 @@ def run_train(args, rank, world, device, outputs=None):
         outputs.update({k: v.detach().float().cpu() for k, v in train_outputs(engine, trainer, last).items()})
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     spread = [round(per_step[0], 2), round(statistics.median(per_step), 2), round(per_step[-1], 2)] if per_step else None
-    # what the HOST needs per step, outside the timed region: with the device idle at the start of a step nothing the host does
-    # can block on a full launch queue (inside a pipelined loop a host that runs ahead waits in hipGraphLaunch, so its loop time
-    # only mirrors the device's). A replayed step needs ~5 ms of host time against ~33 ms of device time (tools/host_step_breakdown.py)
-    host_ms = 0.0
-    for i in range(5):
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        engine.step(next_batch(i))
-        host_ms += (time.perf_counter() - t1) * 1e3 / 5
-    torch.cuda.synchronize()
-    _log(f'timed region: {args.steps} steps in {dt:.3f}s; device-side step ms min/median/max {spread}; host needs '
-         f'{host_ms:.2f} ms/step (device idle at step start); clocks {clocks.summary()}')
-    allreduce = None
-    if world > 1:
-        # the one collective of the path, on its own -- the flat fp32 gradient bucket over RCCL/xGMI (latency-bound at
-        # 4.5 MB). Timed on a scratch copy so the optimiser state of the run is untouched; bus bandwidth = 2(N-1)/N x bytes / time.
-        scratch = engine.bucket.flat.clone()
-        for _ in range(5):
-            torch.distributed.all_reduce(scratch)
-        _sync_barrier(world)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        n_ar = 50
-        e0.record()
-        for _ in range(n_ar):
-            torch.distributed.all_reduce(scratch)
-        e1.record()
-        torch.cuda.synchronize()
-        us = _max_over_ranks(e0.elapsed_time(e1) * 1e3 / n_ar, world, device)
-        allreduce = dict(bytes=engine.bucket.nbytes, us=round(us, 1),
-                         busbw_gbps=round(2.0 * (world - 1) / world * engine.bucket.nbytes / (us * 1e-6) / 1e9, 2),
-                         peak_gbps_per_gpu=7 * 153.0, backend=torch.distributed.get_backend())
-        _log(f'gradient-bucket all-reduce: {allreduce}')
-        del scratch
-    # profiled pass (same workload, same process): per-kernel HIP-event timings of the library kernels
-    recs = []
-    saved_graph, engine._graph = getattr(engine, '_graph', None), None   # events are recorded at launch: eager pass
-    with profiler.profile(recs):
-        for i in range(2):
-            engine.step(batches[i % 2])
-        torch.cuda.synchronize()
-    engine._graph = saved_graph
+    _log(f'timed region: {args.steps} steps in {dt:.3f}s; device-side step ms min/median/max {spread}; '
+         f'clocks {clocks.summary()}')
+    host_ms, allreduce, recs = None, None, []
+    if args.full:
+        host_ms = host_need_ms(engine, next_batch)
+        if world > 1:
+            allreduce = bucket_allreduce(engine, world, device)
+        recs = profiled_train_steps(engine, batches)
     lib_ms = sum(r['total_ms'] for r in recs) / 2
     result = dict(
         metric='edlora_train_images_per_sec_512_sd15', value=round(B * world * args.steps / dt, 4), unit='images/s',
@@ -591,18 +613,19 @@ def run_train(args, rank, world, device, outputs=None):
                     hipgraph=graphed, graph_capture_s=capture_s, channels_last=bool(args.channels_last),
                     host_cores=os.cpu_count(), kernel_source_sha16=kernel_source_fingerprint(),
                     box=box_info(device.index or 0), clocks_timed_region=clocks.summary(), allreduce=allreduce,
-                    host_need_ms_per_step=round(host_ms, 2),
+                    host_need_ms_per_step=None if host_ms is None else round(host_ms, 2),
                     **_tuning_switches()),
         roofline=roofline_from_profile(recs) if recs else None,
         attention_path=attention_path_aggregate(ATTN_PATH_GFLOP_PER_TRAINED_IMAGE, B, recs, 2) if recs else None,
         dominant_kernels_by_name=dominant_by_kernel_name(recs, 2) if recs else None,
         whole_step=whole_step_utilisation(recs, 2, B, dt / args.steps * 1e3) if recs else None,
-        kernels=_kernel_table(recs, 2), library_kernel_ms_per_step=round(lib_ms, 3), step_ms_spread=spread)
+        kernels=_kernel_table(recs, 2), library_kernel_ms_per_step=round(lib_ms, 3) if recs else None,
+        step_ms_spread=spread)
     if data_info is not None:
         result['data_pipeline'] = data_info
         del it, loader
         tmp_dir.cleanup()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result['cpu_baseline'] = cpu_baseline_train(trainer, size)
     del engine, trainer
     torch.cuda.empty_cache()
@@ -752,8 +775,10 @@ def run_regional(args, rank, world, device, steps=None, warmup=None, outputs=Non
     for _ in range(max(0, warmup - 1)):
         sample(graph)
     dt, images = timed(steps)
-    sample(graph, image_out=False)
-    dt_lat, out = timed(steps, image_out=False)
+    dt_lat, out = None, None
+    if args.full:
+        sample(graph, image_out=False)
+        dt_lat, out = timed(steps, image_out=False)
     import numpy as np
     if outputs is not None:
         outputs.update(regional_image=np.asarray(images[0], dtype=np.float32), regional_latents=out.float().cpu())
@@ -761,13 +786,15 @@ def run_regional(args, rank, world, device, steps=None, warmup=None, outputs=Non
     eager_steps = int(getattr(pipe, 'last_call_replay_from', 1)) if graphed else 50     # (read before the profiled eager pass)
     img_ok = (len(images) == 1 and images[0].size == (W, H) and bool(np.isfinite(np.asarray(images[0], dtype=np.float32)).all()))
     recs = []
-    with profiler.profile(recs):                     # HIP events are recorded at launch: profiled pass runs eagerly
-        sample(False)
-        torch.cuda.synchronize()
+    if args.full:
+        with profiler.profile(recs):                 # HIP events are recorded at launch: profiled pass runs eagerly
+            sample(False)
+            torch.cuda.synchronize()
     lib_ms = sum(r['total_ms'] for r in recs)
     res = dict(metric=f'regional_sample_latency_ms_50step_{H}x{W}_3regions', value=round(dt / steps * 1e3, 2),
                unit='ms', n_gpus=world, steps=steps, warmup=warmup, ms_per_step=round(dt / steps * 1e3, 2),
-               value_ms_image=round(dt / steps * 1e3, 2), value_ms_latent=round(dt_lat / steps * 1e3, 2),
+               value_ms_image=round(dt / steps * 1e3, 2),
+               value_ms_latent=None if dt_lat is None else round(dt_lat / steps * 1e3, 2),
                cold_call_ms=round(cold_s * 1e3, 1),
                higher_is_better=False, scaling='weak', vs_baseline=None, dtype='fp16', data='synthetic',
                config=dict(workload=('BASELINE.json configs[4]' if (H, W) == (512, 768) else "the reference's shipped example "
@@ -777,7 +804,8 @@ def run_regional(args, rank, world, device, steps=None, warmup=None, outputs=Non
                                     'value_ms_image: T2I-Adapter network forward on a seeded pose image + region weight, VAE '
                                     'decode, PIL out (the reference call); value_ms_latent: precomputed seeded adapter states, '
                                     'latent out (SURVEY 8(d) cfg #5)', height=H, width=W, region_boxes_px=region_px(H, W),
-                           replicas=world, preset=args.preset, finite=bool(torch.isfinite(out).all()) and img_ok,
+                           replicas=world, preset=args.preset,
+                           finite=(out is None or bool(torch.isfinite(out).all())) and img_ok,
                            hipgraph=graphed, graph_reused_across_calls=graphed,
                            steady_state_eager_steps=eager_steps,
                            timed_calls='steady state: same layout as the warm-up calls, UNet graph captured there and replayed '
@@ -791,10 +819,10 @@ def run_regional(args, rank, world, device, steps=None, warmup=None, outputs=Non
                attention_path=attention_path_aggregate(ATTN_PATH_GFLOP_PER_REGIONAL_CALL if (H, W) == (512, 768) else
                                                        regional_attention_gflop(H, W, region_px(H, W)), 50, recs, 1) if recs else None,
                dominant_kernels_by_name=dominant_by_kernel_name(recs, 1) if recs else None,
-               kernels=_kernel_table(recs, 1), library_kernel_ms_per_sample=round(lib_ms, 3))
+               kernels=_kernel_table(recs, 1), library_kernel_ms_per_sample=round(lib_ms, 3) if recs else None)
     del pipe
     torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and H * W <= 512 * 768:     # (a 1024x2048 oracle call takes minutes)
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and H * W <= 512 * 768:     # (a 1024x2048 oracle call takes minutes)
         res['cpu_baseline'] = cpu_baseline_regional(args.preset, H, W)
     return res
 
@@ -920,7 +948,7 @@ def run_fusion(args, rank, world, device, outputs=None):
                                     f'{args.unet_iters} (spatial), saving excluded', preset=args.preset, concepts=n,
                            host_cores=os.cpu_count(), box=box_info(device.index or 0)),
                roofline=fusion_roofline(lsq, gram), kernels=_kernel_table(recs, 1, 10))
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import fusion_ref
         threads = _cpu_threads()
         g = torch.Generator().manual_seed(0)
@@ -1128,10 +1156,14 @@ def main():
                     help='train: device-resident synthetic batches (the metric) or, SURVEY 8(f).4, batches decoded from JPEG '
                          'through the dataset / transform chain by DataLoader workers inside the timed region')
     ap.add_argument('--workers', type=int, default=8, help='--data jpeg: DataLoader worker processes')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline value does not need: host-need and all-reduce timings, the profiled '
+                    'pass behind roofline and the kernel tables, the CPU baselines, the regional half of the train line, '
+                    'the latent-out regional timing, the parity figures and the verbose record')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baselines')
     ap.add_argument('--height', type=int, default=512, help='regional mode: image height (1024 with --width 2048 = the shipped example)')
     ap.add_argument('--width', type=int, default=768)
-    ap.add_argument('--no-regional', action='store_true', help='train mode: skip the regional-sample half of the metric')
+    ap.add_argument('--no-regional', action='store_true', help='--full, train mode: skip the regional-sample half of the metric')
     ap.add_argument('--channels-last', type=int, default=1, help='NHWC UNet/VAE (the product default)')
     ap.add_argument('--graph', type=int, default=1, help='train: forward+backward replayed from a hipGraph (the product '
                     'default, train_edlora.py); 0 = eager')
@@ -1142,8 +1174,13 @@ def main():
     ap.add_argument('--unet-iters', type=int, default=50)
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32/64); '
-                    'the run uses deterministic convolution solvers (slower) so that its outputs repeat exactly')
+                    'the run uses deterministic convolution solvers (slower) so that its outputs repeat exactly; implies --full')
     args = ap.parse_args()
+    if args.dump_outputs:
+        # the dump holds the outputs of the whole --full sequence, the regional sample's included; that sample's pipeline draws
+        # its new concept-token rows from the global RNG after the train CPU baseline has drawn from it (once per step the
+        # baseline fits in its time bound), so leaving a step out would change them
+        args.full = True
     if args.steps is None:
         args.steps = 2 if args.mode == 'fusion' else 8
     if args.warmup is None:
@@ -1167,7 +1204,7 @@ def main():
     outputs = {} if args.dump_outputs else None
     if args.mode == 'train':
         res = run_train(args, rank, world, device, outputs)
-        if world == 1 and not args.no_regional:
+        if world == 1 and args.full and not args.no_regional:
             reg = run_regional(args, rank, world, device, steps=min(args.steps, 3), warmup=min(args.warmup, 1), outputs=outputs)
             res['regional'] = dict(value_ms=reg['value'], value_ms_image=reg['value_ms_image'],
                                    value_ms_latent=reg['value_ms_latent'], cold_call_ms=reg['cold_call_ms'],
@@ -1183,11 +1220,12 @@ def main():
         res = run_regional(args, rank, world, device, outputs=outputs)
     else:
         res = run_fusion(args, rank, world, device, outputs)
-    res['parity'] = parity_figures()
+    if args.full:
+        res['parity'] = parity_figures()
     if rank == 0:
         if outputs is not None:
             dump_outputs(args.dump_outputs, outputs)
-        full = write_full_record(res)
+        full = write_full_record(res) if args.full else None
         sys.stderr.flush()
         print(compact_line(res, full), flush=True)      # the LAST stdout line, <= COMPACT_LIMIT bytes
     if world > 1:

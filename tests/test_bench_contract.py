@@ -264,3 +264,44 @@ def test_bench_selects_deterministic_kernels():
         else:
             os.environ['MIOPEN_USER_DB_PATH'] = saved_db
 
+
+
+@pytest.mark.parametrize('extra, full', [([], False), (['--full'], True), (['--dump-outputs', 'DUMP'], True),
+                                         (['--full', '--no-regional'], True)])
+def test_plain_run_does_only_what_the_headline_needs(monkeypatch, tmp_path, capsys, extra, full):
+    """A plain `bench.py --steps N --warmup W` times the train step and prints its line; the regional half, the parity figures
+    and the verbose record only come with --full, which --dump-outputs implies. main() on the host, its parts stubbed."""
+    import sys
+    import torch
+    import bench
+    from mixofshow.parallel import dp
+    calls = []
+
+    def part(name, **res):
+        def f(args, *a, **kw):
+            calls.append((name, args.full))
+            return dict(metric=name, value=1.0, unit='u', ms_per_step=1.0, config={}, **res)
+        return f
+
+    monkeypatch.setattr(torch.cuda, 'is_available', lambda: True)
+    monkeypatch.setattr(torch.cuda, 'set_device', lambda d: None)
+    monkeypatch.setattr(dp, 'init_distributed', lambda: (0, 1, 0))
+    monkeypatch.setattr(bench, 'run_train', part('train'))
+    monkeypatch.setattr(bench, 'run_regional', part('regional', value_ms_image=2.0, value_ms_latent=3.0, cold_call_ms=4.0,
+                                                    steps=1, warmup=0, roofline=None, attention_path=None, kernels=[],
+                                                    library_kernel_ms_per_sample=None))
+    monkeypatch.setattr(bench, 'parity_figures', lambda: calls.append(('parity', None)))
+    monkeypatch.setattr(bench, 'write_full_record', lambda res: calls.append(('record', None)) or 'record.json')
+    monkeypatch.setattr(bench, 'deterministic_kernels', lambda: calls.append(('deterministic', None)))
+    monkeypatch.setattr(bench, 'dump_outputs', lambda path, outputs: calls.append(('dump', None)))
+    extra = [str(tmp_path) if a == 'DUMP' else a for a in extra]
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '3', '--warmup', '1'] + extra)
+    bench.main()
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    assert line['metric'] == 'train' and line['value'] == 1.0 and line['ms_per_step'] == 1.0
+    names = [n for n, _ in calls]
+    assert ('train', full) in calls and all(f == full for n, f in calls if n in ('train', 'regional'))
+    assert ('regional' in names) == (full and '--no-regional' not in extra)
+    assert ('parity' in names) == ('record' in names) == full
+    assert (line['full_record'] is not None) == full
+    assert ('deterministic' in names) == ('dump' in names) == ('--dump-outputs' in extra)

@@ -24,7 +24,8 @@ def run(setting, half, steps, warmup, timeout):
     for kv in setting.split():
         k, v = kv.split('=', 1)
         env[k] = v
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--no-cpu-baseline', '--steps', str(steps), '--warmup', str(warmup)]
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--no-cpu-baseline', '--steps', str(steps), '--warmup',
+           str(warmup)]
     cmd += ['--no-regional'] if half == 'train' else ['--mode', 'regional']
     t0 = time.time()
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)

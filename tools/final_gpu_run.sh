@@ -35,19 +35,19 @@ if python -c "import json,sys; d=json.load(open('$O/${TAG}_pmc_traffic.json')); 
 else echo "PMC FAILED"; tail -5 "$O/${TAG}_pmc_run.log"; fi
 fi
 echo "== 3. default bench"
-timeout 900 python bench.py --steps 20 --warmup 5 > "$O/${TAG}_bench_train_n1.json" 2> "$O/${TAG}_bench_train_n1.err"
+timeout 900 python bench.py --full --steps 20 --warmup 5 > "$O/${TAG}_bench_train_n1.json" 2> "$O/${TAG}_bench_train_n1.err"
 cp "$O/bench_full.json" "$O/${TAG}_bench_train_n1_full_record.json" 2>/dev/null     # the verbose record (kernel tables, per-case parity) of that line
 grep -E "timed region|captured" "$O/${TAG}_bench_train_n1.err" | cut -c1-330; wc -c "$O/${TAG}_bench_train_n1.json"; cut -c1-400 "$O/${TAG}_bench_train_n1.json"
 cd /tmp && export TMPDIR=/tmp
 echo "== 4. rocprofv3 kernel stats: train"
 rm -rf /tmp/prof
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o b -- python "$ROOT/bench.py" --steps 6 --warmup 2 --no-cpu-baseline --no-regional \
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o b -- python "$ROOT/bench.py" --full --steps 6 --warmup 2 --no-cpu-baseline --no-regional \
     > "$O/${TAG}_bench_train_under_rocprof.json" 2> "$O/${TAG}_rocprof.err"
 f=$(find /tmp/prof -name "*kernel_stats.csv" | head -1)
 [ -n "$f" ] && head -100 "$f" > "$O/${TAG}_rocprofv3_kernel_stats_bench_train.csv"
 echo "== rocprofv3 kernel stats: regional"
 rm -rf /tmp/prof2
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof2 -o b -- python "$ROOT/bench.py" --mode regional --steps 3 --warmup 1 --no-cpu-baseline \
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof2 -o b -- python "$ROOT/bench.py" --full --mode regional --steps 3 --warmup 1 --no-cpu-baseline \
     > "$O/${TAG}_bench_regional_under_rocprof.json" 2> "$O/${TAG}_rocprof_regional.err"
 f=$(find /tmp/prof2 -name "*kernel_stats.csv" | head -1)
 [ -n "$f" ] && head -100 "$f" > "$O/${TAG}_rocprofv3_kernel_stats_bench_regional.csv"
@@ -56,14 +56,14 @@ grep -E "attn_bwd_dkdv(_pipe)?_kernelIDF16_Li40|conv3x3_(nhwc|halo)_kernel|gn_co
 grep -E "attn_fwd_kernelIDF16_Li40|region_attn_kernel|gn_col_kernel" "$O/${TAG}_rocprofv3_kernel_stats_bench_regional.csv" | cut -c1-160 | head -8
 cut -c1-200 "$O/${TAG}_bench_train_under_rocprof.json"; cut -c1-200 "$O/${TAG}_bench_regional_under_rocprof.json"
 echo "== 5b. the reference's shipped regional example, 1024x2048"
-timeout 400 python bench.py --mode regional --height 1024 --width 2048 --steps 2 --warmup 1 > "$O/${TAG}_bench_regional_1024x2048.json" 2> "$O/${TAG}_bench_regional_1024x2048.err"
+timeout 400 python bench.py --full --mode regional --height 1024 --width 2048 --steps 2 --warmup 1 > "$O/${TAG}_bench_regional_1024x2048.json" 2> "$O/${TAG}_bench_regional_1024x2048.err"
 cp "$O/bench_full.json" "$O/${TAG}_bench_regional_1024x2048_full_record.json" 2>/dev/null; cut -c1-260 "$O/${TAG}_bench_regional_1024x2048.json"
 echo "== 5. train step fed by the JPEG data pipeline (SURVEY 8(f).4)"
-timeout 150 python bench.py --steps 20 --warmup 5 --data jpeg --no-cpu-baseline --no-regional > "$O/${TAG}_bench_train_jpeg.json" 2> "$O/${TAG}_bench_train_jpeg.err"
+timeout 150 python bench.py --full --steps 20 --warmup 5 --data jpeg --no-cpu-baseline --no-regional > "$O/${TAG}_bench_train_jpeg.json" 2> "$O/${TAG}_bench_train_jpeg.err"
 tail -1 "$O/${TAG}_bench_train_jpeg.err"; cut -c1-200 "$O/${TAG}_bench_train_jpeg.json"
 echo "== 2b. PMC of the halo convolution (one shape: B4 320->320 64x64) and of the materialised-probability kernels"
 PMC_BENCH_ARGS="--ref 0" bash tools/pmc_collect.sh conv1,probs > "$O/${TAG}_pmc_conv_run.log" 2>&1
 cp "$O/pmc_conv1,probs.txt" "$O/${TAG}_pmc_conv_halo_and_probs_kernels.txt" 2>/dev/null; grep -A16 "conv3x3_halo_kernel f16" "$O/${TAG}_pmc_conv_halo_and_probs_kernels.txt" | head -40
 echo "== 6. configs[3]: gradient fusion of 14 synthetic ED-LoRAs"
-timeout 420 python bench.py --mode fusion --concepts 14 --steps 2 --warmup 1 > "$O/${TAG}_bench_fusion.json" 2> "$O/${TAG}_bench_fusion.err"
+timeout 420 python bench.py --full --mode fusion --concepts 14 --steps 2 --warmup 1 > "$O/${TAG}_bench_fusion.json" 2> "$O/${TAG}_bench_fusion.err"
 echo "rc=$?"; cp "$O/bench_full.json" "$O/${TAG}_bench_fusion_full_record.json" 2>/dev/null; grep "fusion pass" "$O/${TAG}_bench_fusion.err"; cut -c1-300 "$O/${TAG}_bench_fusion.json"

@@ -46,6 +46,8 @@ struct ConvArgs {
     float* gn_part;               // halo form only, or NULL: per-(pixel tile, output channel) sum and sum of squares of the stored values
     int ksplit, kt_per;           // split-K form: K tiles [z * kt_per, (z + 1) * kt_per) per workgroup, z < ksplit
     float* partial;               // split-K form: fp32 partial sums [ksplit][M][Cout]
+    int lr_nimg, lr_tr, lr_tpi, lr_hwp, lr_npw;   // low-resolution form only (mos_conv_lowres.inc): images / rows per pixel tile, tiles
+                                  // per image, halo row width, halo DMA pieces per wave; kt_per then counts channel chunks
 };
 
 template <int N>
@@ -582,6 +584,8 @@ inline int conv_ksplit(int M, int Cout, int Cin, int* kt_per) {
     return (nk + per - 1) / per;
 }
 
+#include "mos_conv_lowres.inc"
+
 template <typename T, int BM, int BN, bool UP, int S2 = 0>
 int launch_conv_split(ConvArgs a, hipStream_t st) {
     constexpr int NS = 3;
@@ -647,7 +651,9 @@ int launch_conv_cfg(const ConvArgs& a, hipStream_t st) {
 constexpr int RING_MAX_WG = 640;
 
 // Dispatch (round 5, profiles/r05c1_wide_tiles.txt, same box, forward / backward-data in us):
-//   * low-resolution levels (<= 320 tiles of 64 x 64, K >= 36 tiles): split-K raster form;
+//   * low-resolution levels (<= 320 tiles of 64 x 64, K >= 36 tiles): split-K -- stride 1 without the upsampled read on the
+//     row-tile form of mos_conv_lowres.inc where conv_lowres_plan accepts the shape (halo staged once per chunk, weights
+//     streamed; see DESIGN.md 4 / 8 for what it measured), everything else (upsampled read, stride 2) on the raster split-K form;
 //   * maps at least 16 wide and 8 high: the HALO-staged form, 8 x 16 pixels x 64 outputs per workgroup (two workgroups per CU):
 //     B4 320->320 64x64 46/48 -> 38/40, 960->320 133/129 -> 109/104, 640->640 32x32 55/58 -> 43/43, 1920->640 162/101 -> 123/104,
 //     128->128 512x512 416/425 -> 388/354, B2 640->640 32x48 42/46 -> 32/32; the 16 x 16 x 128 tile only where >= 512 input channels
@@ -691,6 +697,8 @@ int launch_conv(ConvArgs a, hipStream_t st) {
     MosProfScope prof(st, "conv3x3", key, 2.0 * a.M * (double)a.Cout * 9.0 * a.Cin,
                       2.0 * ((double)a.M * a.Cin / (a.up ? 4 : 1) + 9.0 * a.Cin * a.Cout + (double)a.M * a.Cout * (a.R ? 2 : 1)));
     if (ks > 1) {
+        LowresPlan lp;
+        if (!a.up && conv_lowres_plan(a.B, a.H, a.Wd, a.Cin, a.Cout, &lp)) return launch_conv_lowres<T>(a, lp, st);
         a.ksplit = ks; a.kt_per = kt_per;
         return a.up ? launch_conv_split<T, 64, 64, true>(a, st) : launch_conv_split<T, 64, 64, false>(a, st);
     }
@@ -724,7 +732,10 @@ int64_t mos_conv3x3_nhwc_workspace_bytes(int B, int H, int W, int Cin, int Cout)
     int kt_per = 0;
     const int64_t M = (int64_t)B * H * W;
     if (M > (1 << 20)) return 0;
-    const int ks = conv_ksplit((int)M, Cout, Cin, &kt_per);
+    int ks = conv_ksplit((int)M, Cout, Cin, &kt_per);
+    // the entry point does not know whether the read is upsampled or strided: enough for whichever split form launch_conv picks
+    LowresPlan lp;
+    if (ks > 1 && conv_lowres_plan(B, H, W, Cin, Cout, &lp) && lp.ksplit > ks) ks = lp.ksplit;
     return ks > 1 ? (int64_t)ks * M * Cout * (int64_t)sizeof(float) : 0;
 }
 

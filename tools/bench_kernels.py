@@ -256,7 +256,7 @@ def gram_case(n, cin, cout, dtype, iters):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=20)
-    ap.add_argument('--only', default='', help="'' = everything, or a comma-separated subset of attn,gemm,region,gram,conv,blas,ff,ffgemm,ffsweep,gn,gnpre,conv1,convvae,convvae1,convs2,probs")
+    ap.add_argument('--only', default='', help="'' = everything, or a comma-separated subset of attn,gemm,region,gram,conv,blas,ff,ffgemm,ffsweep,gn,gnpre,conv1,convlow,convvae,convvae1,convs2,probs")
     ap.add_argument('--dtype', default='f16')
     ap.add_argument('--legacy', type=int, default=0, help='gemm: also time the round-1 multi-launch LoRA path')
     ap.add_argument('--ref', type=int, default=1, help='0: skip the MIOpen / hipBLASLt reference timings')
@@ -304,6 +304,8 @@ def main():
         conv_s2_reference([(4, 128, 512, 512, 2), (4, 256, 256, 256, 2), (4, 512, 128, 128, 2), (4, 320, 64, 64, 1),
                            (4, 640, 32, 32, 1), (4, 1280, 16, 16, 1), (2, 320, 64, 96, 1), (2, 640, 32, 48, 1),
                            (2, 1280, 16, 24, 1)], dt, args.iters)
+    if 'convlow' in only:        # the two low-resolution split-K shapes of a training batch alone: clean per-launch PMC counters
+        conv_reference([(4, 1280, 1280, 8, 8), (4, 1280, 1280, 16, 16)], dt, args.iters, ref=False)
     if 'conv1' in only:          # ONE shape (level-0 ResNet conv, forward + backward-data): clean per-launch PMC counters
         conv_reference([(4, 320, 320, 64, 64)], dt, args.iters, ref=False)
     if 'convvae1' in only:       # ONE VAE shape on the 16 x 16 x 128 / 32-channel-chunk tile: clean per-launch PMC counters

@@ -11,7 +11,7 @@ def short(name):
     m = re.search(r'(attn_fwd_kernel|attn_bwd_dq_kernel|attn_bwd_dkdv_kernel|attn_bwd_dkdv_pipe_kernel|region_attn_kernel|'
                   r'conv3x3_halo_kernel|attn_probs_kernel|attn_pv_kernel|gn_col_kernel|'
                   r'gemm_lora_kernel|conv3x3_nhwc_kernel|gn_nhwc_reduce_kernel|gn_nhwc_apply_kernel|lora_grad_kernel|'
-                  r'gram_kernel|lsq_grad_mfma_kernel)', name)
+                  r'gram_kernel|lsq_grad_mfma_kernel|conv3x3_lowres_kernel|conv_splitk_reduce_kernel)', name)
     if not m:
         return None
     dt = re.search(r'I(DF16_|DF16b)', name)

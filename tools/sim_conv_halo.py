@@ -146,6 +146,211 @@ def run_halo(x, w, TH, BN, up=False, CK=64):
     return y
 
 
+# ---- conv3x3_lowres_kernel (csrc/mos_conv_lowres.inc): row tiles of up to 256 pixels, halo staged once per chunk, split-K ----
+LR_BN, LR_PIX, LR_HRMAX, LR_NS = 64, 256, 448, 3
+B128_GROUPS = [list(range(0, 4)) + list(range(12, 16)) + list(range(20, 28)), list(range(4, 12)) + list(range(16, 20)) + list(range(28, 32)),
+               list(range(32, 36)) + list(range(44, 48)) + list(range(52, 60)), list(range(36, 44)) + list(range(48, 52)) + list(range(60, 64))]
+
+
+def conv_ksplit(M, Cout, Cin):
+    """conv_ksplit of mos_conv.hip: (ranges, K tiles per range) of the raster split-K form; ranges 1 = not split."""
+    nk = 9 * (Cin // 64)
+    if nk < 36:
+        return 1, 0
+    tiles = ((M + 63) // 64) * ((Cout + 63) // 64)
+    if tiles > 320:
+        return 1, 0
+    ks = min((640 + tiles - 1) // tiles, nk // 6)
+    if ks < 2:
+        return 1, 0
+    per = (nk + ks - 1) // ks
+    return (nk + per - 1) // per, per
+
+
+def lowres_plan(B, H, Wd, Cin, Cout):
+    """conv_lowres_plan: the geometry and the chunk ranges, or None where the shape keeps the raster split-K form."""
+    if conv_ksplit(B * H * Wd, Cout, Cin)[0] <= 1 or Wd > 64:
+        return None
+    hwp = Wd + 2 + (6 if Wd % 8 == 4 else 0)
+    nimg, tr = 1, H
+    if H * Wd <= LR_PIX:
+        nimg = min(LR_PIX // (H * Wd), LR_HRMAX // ((H + 2) * hwp), B)
+    else:
+        tr = LR_PIX // Wd
+        while tr > 0 and (tr + 2) * hwp > LR_HRMAX:
+            tr -= 1
+    if nimg < 1 or tr < 1:
+        return None
+    p = dict(nimg=nimg, tr=tr, hwp=hwp, tpi=(H + tr - 1) // tr, blk=(tr + 2) * hwp)
+    p['hr'] = nimg * p['blk']
+    p['npw'] = ((p['hr'] + 7) // 8 + 3) // 4
+    p['mt'] = ((B + nimg - 1) // nimg) * p['tpi']
+    cpt, units = Cin // 64, p['mt'] * ((Cout + LR_BN - 1) // LR_BN)
+    ks = min(256 // units, cpt // 2)
+    if ks < 2:
+        return None
+    p['cpz'] = (cpt + ks - 1) // ks
+    p['ksplit'] = (cpt + p['cpz'] - 1) // p['cpz']
+    return p if p['ksplit'] >= 2 else None
+
+
+def lowres_lane_pixel(p, H, Wd, B, m_tile, wave, i, l15):
+    """(output row m or -1, halo row of tap (0, 0)) of MFMA column l15 of pixel fragment i."""
+    b0, y0 = (m_tile // p['tpi']) * p['nimg'], (m_tile % p['tpi']) * p['tr']
+    pb = p['tr'] * Wd
+    pt = wave * 64 + i * 16 + ((l15 + 12) & 15)
+    img, prem = divmod(pt, pb)
+    py, px = divmod(prem, Wd)
+    ok = img < p['nimg'] and b0 + img < B and y0 + py < H
+    return (((b0 + img) * H + y0 + py) * Wd + px if ok else -1), (img * p['blk'] + py * p['hwp'] + px if ok else 0)
+
+
+def lowres_bank_conflicts(p, H, Wd, B):
+    """Worst number of distinct addresses on one 16-byte bank slot within a ds_read_b128 lane group, over every halo fragment read
+    (tile, wave, fragment, tap, k-half) of the geometry whose lanes all hold pixels of the map; 1 = conflict-free."""
+    worst = 1
+    for m_tile in range(p['mt']):
+        for wave in range(4):
+            for i in range(4):
+                px = [lowres_lane_pixel(p, H, Wd, B, m_tile, wave, i, l15) for l15 in range(16)]
+                if any(m < 0 for m, _ in px):
+                    continue
+                for tap in range(9):
+                    for kk in range(2):
+                        for grp in B128_GROUPS:
+                            slots = {}
+                            for lane in grp:
+                                l15, lg = lane & 15, lane >> 4
+                                hrow = px[l15][1] + (tap // 3) * p['hwp'] + tap % 3
+                                addr = (hrow * CBK + (((kk * 4 + lg) ^ (hrow & 7)) * 8)) * 2
+                                slots.setdefault((addr // 16) % 16, set()).add(addr)
+                            worst = max(worst, max(len(v) for v in slots.values()))
+    return worst
+
+
+def run_lowres(x, w, ldx_pad=0):
+    """x (B, H, W, C) NHWC, w (Cout, 3, 3, C): y (B, H, W, Cout) as conv3x3_lowres_kernel + the ordered sum over the chunk ranges
+    compute it. ldx_pad: extra channels per pixel in memory (the channel-slice read: ldx = C + ldx_pad). Every DMA is asserted in
+    range or out of range under both readings of the bounds rule (gload), every destination inside its buffer."""
+    B, H, Wd, C = x.shape
+    N = w.shape[0]
+    K = 9 * C
+    p = lowres_plan(B, H, Wd, C, N)
+    assert p is not None, 'the shape keeps the raster split-K form'
+    nimg, tr, hwp, npw, tpi, blk, HR = p['nimg'], p['tr'], p['hwp'], p['npw'], p['tpi'], p['blk'], p['hr']
+    LX = C + ldx_pad
+    xm = np.full((B, H, Wd, LX), 1e6)                  # (the padding channels would wreck the sum if a DMA touched them)
+    xm[..., :C] = x
+    xg = xm.reshape(-1)[:(B * H * Wd - 1) * LX + C].astype(np.float64)
+    wg = w.reshape(-1).astype(np.float64)
+    xlimit, wlimit = ((B * H * Wd - 1) * LX + C) * 2, ((N - 1) * K + K) * 2
+    HB = LR_HRMAX * CBK
+    cpt, nt = C // CBK, (N + LR_BN - 1) // LR_BN
+    OOBL = 0x80000000
+    M = B * H * Wd
+    partial = np.full((p['ksplit'], M, N), np.nan)     # no zero-fill: every element must be written
+
+    def gload(mem, lane_off, uni_off, limit_bytes):
+        a_ = lane_off >= limit_bytes
+        b_ = lane_off >= limit_bytes - uni_off
+        assert a_ == b_, (lane_off, uni_off, limit_bytes)
+        if a_:
+            return np.zeros(8)
+        o = lane_off + uni_off
+        assert 0 <= o and o + 16 <= limit_bytes
+        return mem[o // 2: o // 2 + 8]
+
+    for m_tile in range(p['mt']):
+        b0, y0 = (m_tile // tpi) * nimg, (m_tile % tpi) * tr
+        for n_tile in range(nt):
+            n0 = n_tile * LR_BN
+            for zsplit in range(p['ksplit']):
+                c0 = zsplit * p['cpz']
+                c1 = min(cpt, c0 + p['cpz'])
+                lds_h = np.full(2 * HB, np.nan)
+                lds_w = np.full(LR_NS * LR_BN * CBK, np.nan)
+
+                def hoff(wave, lane, i):
+                    hr = (wave + 4 * i) * 8 + lane // 8
+                    img, rem = divmod(hr, blk)
+                    hy, hx = divmod(rem, hwp)
+                    bb, yy, xx = b0 + img, y0 + hy - 1, hx - 1
+                    lc = (lane % 8) ^ (hr & 7)
+                    ok = hr < HR and bb < B and 0 <= yy < H and 0 <= xx < Wd
+                    return (((bb * H + yy) * Wd + xx) * LX + lc * 8) * 2 if ok else OOBL
+
+                def issue_halo(cch, hb):
+                    live = cch < c1
+                    limit = xlimit if live else 0
+                    cb = cch * CBK * 2 if live else 0
+                    for wave in range(4):
+                        for i in range(npw):
+                            base = hb * HB + (wave + 4 * i) * 512
+                            assert base + 512 <= (hb + 1) * HB
+                            for lane in range(64):
+                                lds_h[base + lane * 8: base + lane * 8 + 8] = gload(xg, hoff(wave, lane, i), cb, limit)
+
+                def issue_w(cch, tap, buf):
+                    live = cch < c1
+                    limit = wlimit if live else 0
+                    kb = (tap * C + cch * CBK) * 2 if live else 0
+                    for wave in range(4):
+                        for i in range(2):
+                            base = buf * LR_BN * CBK + wave * 512 + i * 2048
+                            for lane in range(64):
+                                q = wave * 64 + lane + 256 * i
+                                row = q // 8
+                                wo = ((n0 + row) * K + ((q % 8) ^ (row & 7)) * 8) * 2
+                                lds_w[base + lane * 8: base + lane * 8 + 8] = gload(wg, wo, kb, limit)
+
+                acc = np.zeros((4, 4, 4, 64, 4))       # [wave][j][i][lane][r]
+                px = [[[lowres_lane_pixel(p, H, Wd, B, m_tile, wave, i, l15) for l15 in range(16)] for i in range(4)] for wave in range(4)]
+                issue_halo(c0, 0)
+                for cch in range(c0, c1):
+                    hbuf = (cch - c0) & 1
+                    issue_halo(cch + 1, 1 - hbuf)
+                    for tap in range(9):
+                        wbuf = ((cch - c0) * 9 + tap) % LR_NS      # the ring: tile t in buffer t % NS
+                        issue_w(cch, tap, wbuf)
+                        for wave in range(4):
+                            for kk in range(2):
+                                bfr = np.zeros((4, 64, 8)); afr = np.zeros((4, 64, 8))
+                                for lane in range(64):
+                                    l15, lg = lane & 15, lane >> 4
+                                    for i in range(4):
+                                        hrow = px[wave][i][l15][1] + (tap // 3) * hwp + tap % 3
+                                        a0 = hbuf * HB + hrow * CBK + (((kk * 4 + lg) ^ (hrow & 7)) * 8)
+                                        assert a0 + 8 <= (hbuf + 1) * HB
+                                        bfr[i, lane] = lds_h[a0:a0 + 8]
+                                    for j in range(4):
+                                        a0 = wbuf * LR_BN * CBK + l15 * CBK + j * 16 * CBK + ((kk * 4 + lg) ^ (l15 & 7)) * 8
+                                        afr[j, lane] = lds_w[a0:a0 + 8]
+                                for j in range(4):
+                                    for i in range(4):
+                                        if all(m < 0 for m, _ in px[wave][i]):
+                                            continue           # (a fragment off the map: its reads were checked, its sum is dropped)
+                                        a4 = [list(r_) for r_ in acc[wave, j, i]]
+                                        mfma16(a4, np.nan_to_num(afr[j]), np.nan_to_num(bfr[i], nan=1e6))
+                                        acc[wave, j, i] = a4
+                    if cch == c1 - 1:
+                        issue_w(c1, 0, (wbuf + 1) % LR_NS)  # a weight tile past the range: zeros through the dead descriptor
+                for wave in range(4):
+                    for j in range(4):
+                        for i in range(4):
+                            for lane in range(64):
+                                l15, lg = lane & 15, lane >> 4
+                                n = n0 + j * 16 + lg * 4
+                                m = px[wave][i][l15][0]
+                                if m >= 0 and n < N:
+                                    assert np.isnan(partial[zsplit, m, n:n + 4]).all(), 'written twice'
+                                    partial[zsplit, m, n:n + 4] = acc[wave, j, i, lane]
+    assert not np.isnan(partial).any(), 'a partial element was never written'
+    y = np.zeros((M, N))
+    for z in range(p['ksplit']):
+        y += partial[z]
+    return y.reshape(B, H, Wd, N)
+
+
 if __name__ == '__main__':
     g = torch.Generator().manual_seed(0)
     for (B, H, Wd, C, N, TH, BN, CK) in ((1, 8, 16, 64, 64, 8, 64, 64), (2, 10, 20, 128, 64, 8, 64, 64), (1, 17, 33, 64, 128, 16, 128, 64),
